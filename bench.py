@@ -4,6 +4,8 @@
 Contract (driver):  python bench.py --gpus N --steps K --warmup W
   N>1 is launched by the driver through torch.distributed.run (one rank per GPU, RCCL).
   Prints ONE JSON line from rank 0.
+  --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned (total loss + loss terms)
+  and a seeded sample of the parameters it left as DIR/<name>.npy; the inputs are seeded, so two builds can be compared.
 
 A "step" = one full training step of BASELINE.json configs[1]: S2ANet-R50-FPN, 4 synthetic
 1024x1024 DOTA-shaped tiles per GPU, fp32: backbone+FPN (MIOpen), S2ANetHead with the
@@ -716,12 +718,13 @@ def make_batches(n, batch, rank, ncls, device, mf, orcnn):
 def timed_region(runner, batches, steps, rdist, device):
     """EXACTLY `steps` train steps between barrier + synchronize on both sides; max over ranks.  Also returns the host
     time the loop took to ENQUEUE the steps (before the closing synchronize): enqueue ~ total means the host, not the
-    GPU, paces the step -- the number that explains a flat multi-GPU curve with one Python process per GPU."""
+    GPU, paces the step -- the number that explains a flat multi-GPU curve with one Python process per GPU -- and the
+    loss terms of the last step."""
     rdist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(steps):
-        loss, _ = runner.train_step(*batches[i % len(batches)])
+        loss, parsed = runner.train_step(*batches[i % len(batches)])
     t_enq = time.perf_counter() - t0
     torch.cuda.synchronize()
     rdist.barrier()
@@ -729,7 +732,25 @@ def timed_region(runner, batches, steps, rdist, device):
     dt = rdist.all_reduce_max(dt, device)
     loss_v = float(loss.detach())
     assert np.isfinite(loss_v), "non-finite loss"
-    return dt, loss_v, t_enq
+    return dt, loss_v, t_enq, parsed
+
+
+DUMP_PARAM_SAMPLE = 1 << 20  # parameters written by --dump-outputs: a fixed seeded sample of 1 Mi values (4 MB)
+
+
+def dump_outputs(out_dir, runner, loss_v, parsed):
+    """--dump-outputs DIR: what the last timed step handed its caller -- the total loss (``total_loss.npy``) and every
+    loss term (``<name>.npy``), float64 -- and the model it left behind: ``params_sample.npy``, float32, the values of
+    DUMP_PARAM_SAMPLE positions drawn with seed 0 from all parameters flattened in ``named_parameters()`` order."""
+    import re
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "total_loss.npy"), np.array(loss_v, np.float64))
+    for name, v in parsed.items():
+        np.save(os.path.join(out_dir, re.sub(r"[^A-Za-z0-9_.-]", "_", name) + ".npy"),
+                np.asarray(v.detach().double().cpu().numpy(), np.float64))
+    flat = torch.cat([p.detach().reshape(-1).float() for _, p in runner.model.named_parameters()])
+    idx = np.sort(np.random.default_rng(0).choice(flat.numel(), min(flat.numel(), DUMP_PARAM_SAMPLE), replace=False))
+    np.save(os.path.join(out_dir, "params_sample.npy"), flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy())
 
 
 def extra_leg(model, amp, mf, steps, rank, device, rdist, bf16_params):
@@ -747,7 +768,7 @@ def extra_leg(model, amp, mf, steps, rank, device, rdist, bf16_params):
     bs = make_batches(N_BATCHES, batch, rank, ncls, device, mf, model == "orcnn_van3")
     for i in range(2 * N_BATCHES):
         r.train_step(*bs[i % N_BATCHES])
-    dt, loss, enq = timed_region(r, bs, steps, rdist, device)
+    dt, loss, enq, _ = timed_region(r, bs, steps, rdist, device)
     out = {"value": batch * steps / dt, "unit": "tiles/s", "ms_per_step": dt / steps * 1e3, "steps": steps,
            "host_enqueue_ms_per_step": enq / steps * 1e3, "final_loss": loss, "tiles_per_step": batch,
            "dtype": "bf16" if amp is not None else "f32"}
@@ -780,7 +801,7 @@ def ddp_overhead_leg(cfg, device, b16, steps, warm, bf16_params, rdist, enq_plai
             assert (r.reducer is not None) if tag == "reducer" else (r.ddp is not r.model)
             for i in range(warm):
                 r.train_step(*b16[i % N_BATCHES])
-            dt, loss, enq = timed_region(r, b16, steps, rdist, device)
+            dt, loss, enq, _ = timed_region(r, b16, steps, rdist, device)
             leg = {"ms_per_step": dt / steps * 1e3, "host_enqueue_ms_per_step": enq / steps * 1e3,
                    "host_overhead_ms": enq / steps * 1e3 - enq_plain_ms, "step_overhead_ms": dt / steps * 1e3 - ms_plain,
                    "final_loss": loss}
@@ -859,7 +880,13 @@ def main():
                          "with find records for the NHWC shapes MIOpen runs its fp32 MFMA implicit-GEMM kernels without "
                          "layout transposes, 52.5 vs 55.3 ms/step (round 3; on heuristics the same layout was 494 ms in "
                          "round 1 -- the packaged records are what makes it the faster one).  contiguous for the others")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (total loss and every loss "
+                         "term, float64) and a fixed seeded sample of the parameters it left (float32) as DIR/<name>.npy; "
+                         "rank 0 only.  The inputs are seeded: two builds run with the same arguments can be compared")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.memory_format is None:
         # (the R101 trunk has fp32 NHWC records for none of its layer3 shapes: it stays NCHW in f32)
         from rs_detection_amd.utils.miopen_db import packaged_records_match
@@ -958,7 +985,10 @@ def main():
         runner.train_step(*timed_batches[i % len(timed_batches)])
     if args.fresh_k:
         timed_batches = timed_batches[args.warmup:]
-    dt, loss_v, t_enq = timed_region(runner, timed_batches, args.steps, rdist, device)
+    dt, loss_v, t_enq, parsed = timed_region(runner, timed_batches, args.steps, rdist, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, runner, loss_v, parsed)
+    del parsed
     # short extra leg of the default line: the same runner on never-seen K tuples (what --fresh-k times in full)
     fresh = None
     if not args.fresh_k and args.model == "s2anet_r50":
@@ -966,7 +996,7 @@ def main():
         fb = fresh_k_batches(batches, nf + 2, rank, ncls, device, orcnn)
         for b_ in fb[:2]:
             runner.train_step(*b_)
-        dtf, _, enqf = timed_region(runner, fb[2:], nf, rdist, device)
+        dtf, _, enqf, _ = timed_region(runner, fb[2:], nf, rdist, device)
         fresh = dict(ms_per_step=dtf / nf * 1e3, steps=nf, host_enqueue_ms_per_step=enqf / nf * 1e3)
         del fb
     BN_DOM = BN_ROW_CL if args.memory_format == "channels_last" else BN_ROW     # the form the timed fp32 step ran
@@ -987,7 +1017,7 @@ def main():
         for i in range(warm16):
             r16.train_step(*b16[i % N_BATCHES])
         steps16 = max(args.steps, 20)
-        dt16, loss16, enq16 = timed_region(r16, b16, steps16, rdist, device)
+        dt16, loss16, enq16, _ = timed_region(r16, b16, steps16, rdist, device)
         bf16_leg = {"value": batch * world * steps16 / dt16, "unit": "tiles/s", "ms_per_step": dt16 / steps16 * 1e3,
                     "steps": steps16, "warmup": warm16, "dtype": "bf16", "memory_format": "channels_last",
                     "bf16_params": bool(r16.bf16_params), "host_enqueue_ms_per_step": enq16 / steps16 * 1e3,

@@ -26,15 +26,6 @@ def oracle_c():
 
 
 @pytest.fixture(scope="session")
-def oracle_ref():
-    import oracle
-    r = oracle.ref()
-    if not r.available:
-        pytest.skip("oracle/_ref not built (needs /root/reference at build time)")
-    return r
-
-
-@pytest.fixture(scope="session")
 def cuda():
     import torch
     if not torch.cuda.is_available():
@@ -65,3 +56,22 @@ def degenerate_boxes():
         [20, 10, 20, 10, 0], [10, 10, 20, 10, np.pi], [500, 500, 30, 30, 0.3], [10, 20, 20, 10, 0],
         [10, 10, 20, 10, 1e-4], [10.00001, 10, 20, 10, 0], [0, 0, 1, 1, 0], [.5, .5, 1, 2, 0],
     ], np.float32)
+
+
+_REF_CONFIGS = None
+
+
+def reference_configs():
+    """{shipped config file name: {section: value}} of the reference's config files, from the stored fixture
+    (tests/golden/ref_configs.json); where the reference itself is present, the fixture is first checked against it."""
+    global _REF_CONFIGS
+    if _REF_CONFIGS is None:
+        import importlib.util
+        spec = importlib.util.spec_from_file_location(
+            "make_config_golden", os.path.join(ROOT, "tests", "golden", "make_config_golden.py"))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        _REF_CONFIGS = mod.load()
+        if os.path.isdir(mod.REF):
+            assert _REF_CONFIGS == mod.from_reference(), "tests/golden/ref_configs.json is stale: re-run make_config_golden.py"
+    return _REF_CONFIGS

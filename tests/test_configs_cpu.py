@@ -1,6 +1,6 @@
 """CPU: every section of every file under configs/ builds through the registries (model, optimizer, scheduler,
 SWA optimizer / scheduler, dataset.train / val / test on generated folders), the shipped configs equal the
-reference's files where the reference is mounted, and the schedules follow the reference's formulas."""
+reference's files (their sections stored in tests/golden/ref_configs.json), and the schedules follow the reference's formulas."""
 import glob
 import math
 import os
@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from conftest import reference_configs
 import rs_detection_amd.data  # noqa: F401
 import rs_detection_amd.models  # noqa: F401
 from rs_detection_amd.config import Config
@@ -19,10 +20,7 @@ from rs_detection_amd.utils.registry import DATASETS, MODELS, OPTIMS, SCHEDULERS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONFIGS = sorted(glob.glob(os.path.join(ROOT, "configs", "*", "*.py")))
-REF = {"s2anet_r50_fpn_1x_dota.py": "/root/reference/configs/s2anet/s2anet_r50_fpn_1x_dota.py",
-       "s2anet_r101_fpn_1x_dota_rotate_balance_ms.py":
-           "/root/reference/projects/s2anet/configs/s2anet_r101_fpn_1x_dota_rotate_balance_ms.py",
-       "orcnn_van3_7_anchor.py": "/root/reference/configs/orcnn_van3_7_anchor_swa_1.py"}
+REF = ["s2anet_r50_fpn_1x_dota.py", "s2anet_r101_fpn_1x_dota_rotate_balance_ms.py", "orcnn_van3_7_anchor.py"]
 
 
 def _make_folder(tmp_path, n=3, size=64):
@@ -84,10 +82,8 @@ def test_every_section_builds(path, tmp_path):
 
 @pytest.mark.parametrize("name", sorted(REF))
 def test_shipped_configs_equal_the_reference(name):
-    if not os.path.exists(REF[name]):
-        pytest.skip("reference not mounted")
     mine = Config([c for c in CONFIGS if os.path.basename(c) == name][0]).dump()
-    theirs = Config(REF[name]).dump()
+    theirs = reference_configs()[name]
     keys = ["model", "optimizer", "scheduler", "max_epoch", "log_interval", "checkpoint_interval"]
     if name.startswith("orcnn"):
         keys += ["optimizer_swa", "scheduler_swa", "swa_start_epoch", "eval_interval", "merge_nms_threshold_type"]

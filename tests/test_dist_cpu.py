@@ -100,11 +100,11 @@ def test_bench_gpus2_self_launches_and_fails_loudly_without_a_gpu():
     """`python bench.py --gpus 2` with no launcher around it: the parent must start the ranks itself (round 1 died on
     an assert here).  On this GPU-less container every rank then refuses to run (no CPU fallback) -> non-zero exit."""
     import subprocess
+    if torch.cuda.device_count() > 0:                # (does not initialise HIP)
+        pytest.skip("GPU present: covered by tests/test_gpu_dist.py")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        env=env, capture_output=True, text=True, timeout=280)
-    if torch.cuda.device_count() > 0:
-        pytest.skip("GPU present: covered by tests/test_gpu_dist.py")
     assert p.returncode != 0 and "AssertionError" not in p.stderr
     assert "needs an MI355X" in p.stderr
 

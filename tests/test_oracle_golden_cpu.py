@@ -1,5 +1,6 @@
 """CPU: the oracle restatement vs (a) committed golden vectors produced from the reference's own
-sources and (b) oracle/_ref itself when it is present.  No GPU, no /root/reference needed."""
+sources and (b) oracle/_ref itself on fresh inputs (its outputs stored in tests/golden/ref_fresh.npz, used when it
+was not built).  No GPU, no /root/reference needed."""
 import os
 
 import numpy as np
@@ -193,26 +194,61 @@ def test_anchor_grid_closed_form():
         start += f * f
 
 
-@pytest.mark.parametrize("v", [0, 1])
-def test_oracle_equals_reference_build(oracle_c, oracle_ref, v):
-    """Fresh random + degenerate inputs: restatement == reference CPU source, bit for bit."""
+def fresh_iou_case(v):
+    """Fresh random + degenerate inputs of the rotated IoU (tests/golden/make_ref_fresh.py stores the reference's output)."""
     rng = np.random.default_rng(99 + v)
-    b1 = np.concatenate([dota_boxes(rng, 150, 250), degenerate_boxes()])
-    b2 = np.concatenate([dota_boxes(rng, 900, 250), degenerate_boxes()])
-    a, e = oracle_c.box_iou_rotated(b1, b2, v), oracle_ref.box_iou_rotated(b1, b2, v)
-    assert (a.view(np.int32) == e.view(np.int32)).all()
-    assert (e > 0).mean() > 0.05
+    return (np.concatenate([dota_boxes(rng, 150, 250), degenerate_boxes()]),
+            np.concatenate([dota_boxes(rng, 900, 250), degenerate_boxes()]))
 
 
-def test_oracle_nms_equals_reference_build(oracle_c, oracle_ref):
+def fresh_nms_cases():
+    """[(dets, order, thr)] of the rotated NMS, 5- and 6-column boxes (same generator as above)."""
     rng = np.random.default_rng(5)
     d = dota_boxes(rng, 400, 200)
     s = rng.uniform(0, 1, 400).astype(np.float32)
     order = np.argsort(-s, kind="stable").astype(np.int32)
-    for thr in (0.05, 0.5):
-        assert (oracle_c.nms_rotated(d, order, thr) == oracle_ref.nms_rotated(d, order, thr)).all()
     d6 = np.concatenate([d, rng.integers(0, 3, (400, 1)).astype(np.float32)], 1)
-    assert (oracle_c.nms_rotated(d6, order, 0.2) == oracle_ref.nms_rotated(d6, order, 0.2)).all()
+    return [(d, order, 0.05), (d, order, 0.5), (d6, order, 0.2)]
+
+
+def reference_build_outputs(ref):
+    """What the reference's own CPU build returns on the fresh cases, under the keys of tests/golden/ref_fresh.npz."""
+    out = {}
+    for v in (0, 1):
+        out["iou_v%d" % v] = ref.box_iou_rotated(*fresh_iou_case(v), v)
+    for i, (d, order, thr) in enumerate(fresh_nms_cases()):
+        out["nms_keep%d" % i] = ref.nms_rotated(d, order, thr)
+    return out
+
+
+@pytest.fixture(scope="module")
+def ref_fresh():
+    """The reference build's outputs on the fresh cases: computed by oracle/_ref where it was built (the stored file is
+    then checked against it), read from tests/golden/ref_fresh.npz otherwise."""
+    stored = dict(load("ref_fresh.npz"))
+    r = oracle.ref()
+    if r.available:
+        live = reference_build_outputs(r)
+        assert sorted(live) == sorted(k for k in stored if k != "provenance")
+        for k, a in live.items():
+            assert a.dtype == stored[k].dtype and (a.view(np.uint8) == stored[k].view(np.uint8)).all(), \
+                "tests/golden/ref_fresh.npz is stale (%s): re-run make_ref_fresh.py" % k
+        return live
+    return stored
+
+
+@pytest.mark.parametrize("v", [0, 1])
+def test_oracle_equals_reference_build(oracle_c, ref_fresh, v):
+    """Fresh random + degenerate inputs: restatement == reference CPU source, bit for bit."""
+    b1, b2 = fresh_iou_case(v)
+    a, e = oracle_c.box_iou_rotated(b1, b2, v), ref_fresh["iou_v%d" % v]
+    assert (a.view(np.int32) == e.view(np.int32)).all()
+    assert (e > 0).mean() > 0.05
+
+
+def test_oracle_nms_equals_reference_build(oracle_c, ref_fresh):
+    for i, (d, order, thr) in enumerate(fresh_nms_cases()):
+        assert (oracle_c.nms_rotated(d, order, thr) == ref_fresh["nms_keep%d" % i]).all()
 
 
 def test_rie_oracle_matches_reference_cpu_source():

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import dota_boxes
+from conftest import dota_boxes, reference_configs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -111,11 +111,9 @@ def test_orcnn_config_matches_reference_and_builds():
     from rs_detection_amd.config import Config
     from rs_detection_amd.utils.registry import MODELS, build_from_cfg
     mine = Config(os.path.join(ROOT, "configs", "orcnn", "orcnn_van3_7_anchor.py"))
-    ref = "/root/reference/configs/orcnn_van3_7_anchor_swa_1.py"
-    if os.path.exists(ref):
-        theirs = Config(ref)
-        for k in ("model", "optimizer", "scheduler", "optimizer_swa", "scheduler_swa", "max_epoch"):
-            assert mine.dump()[k] == theirs.dump()[k], k
+    theirs = reference_configs()["orcnn_van3_7_anchor.py"]          # tests/golden/ref_configs.json
+    for k in ("model", "optimizer", "scheduler", "optimizer_swa", "scheduler_swa", "max_epoch"):
+        assert mine.dump()[k] == theirs[k], k
     cfg = mine.dump()["model"]
     cfg["backbone"] = dict(type="van_b0", img_size=256, num_stages=4, out_indices=(0, 1, 2, 3))
     cfg["neck"]["in_channels"] = [32, 64, 160, 256]
